@@ -137,6 +137,10 @@ def parse_args():
                     help="coefficient all-reduce through the library's own RCCL communicator on the "
                          "compute stream (default; falls back to torch.distributed if its self-check "
                          "fails) or through a torch.distributed callback")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the K timed steps, write what they computed as DIR/<name>.npy (float64): the coefficient set "
+                         "(coefs) and, for a fixed seeded sample of at most 2^18 particles (index: their positions in the "
+                         "caller's order), the positions, velocities, accelerations and potentials (pos, vel, acc, pot)")
     return ap.parse_args()
 
 
@@ -675,6 +679,31 @@ def other_configs(ctx, device, n, which=(2, 3, 4), steps=30, min_seconds=0.0):
 METRIC = "particle-steps/sec (coef+force+kick-drift), 1e8 SphericalSL halo, 1/2/4/8 GPU"
 
 
+DUMP_SAMPLE = 1 << 18        # particles written by --dump-outputs: 2^18 x 11 doubles = 23 MB, under the 64 MB the dump may take
+DUMP_SEED = 4242
+
+
+def dump_outputs(out_dir, comp, force, ntot, first, gather):
+    """--dump-outputs: the coefficients and a fixed sample of the particle state, as a caller of the step receives them
+    (exp_amd_comp_download: the caller's particle order, velocities at the step boundary).  The sample is the same set of
+    particle indices for every run with the same --nbodies, whatever the rank count; this rank holds [first, first + n).
+    gather(obj) -> the list of every rank's obj on rank 0, None elsewhere."""
+    nsamp = min(ntot, DUMP_SAMPLE)
+    idx = (np.sort(np.random.default_rng(DUMP_SEED).choice(ntot, nsamp, replace=False)) if nsamp < ntot
+           else np.arange(ntot))
+    mine = idx[(idx >= first) & (idx < first + comp.n)] - first
+    part = {f: comp.download((f,))[f][mine] for f in ("pos", "vel", "acc", "pot")}
+    parts = gather(part)
+    coefs = force.get_coefs()
+    if parts is None:
+        return
+    arrays = {"coefs": coefs, "index": idx, **{f: np.concatenate([p[f] for p in parts]) for f in part}}
+    assert len(arrays["pos"]) == nsamp
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+
 def _flush_c_stdio():
     """RCCL prints a banner through C stdio; on a pipe it would only come out at exit -- after the
     JSON line, and from every rank under torchrun.  Push it out now."""
@@ -914,6 +943,17 @@ def main():
                   0.5 * (step_ms[len(step_ms) // 2 - 1] + step_ms[len(step_ms) // 2]),
                   "min_ms": step_ms[0], "max_ms": step_ms[-1],
                   "what": "hipEvent time of each of the K timed steps on the context's stream (per-kernel events on)"}
+
+    if args.dump_outputs:
+        # the state right after the K timed steps: the regions below run a clock-dependent number of further steps
+        def gather(obj):
+            if not use_comm:
+                return [obj]
+            objs = [None] * world
+            dist.all_gather_object(objs, obj)
+            return objs if rank == 0 else None
+        dump_outputs(args.dump_outputs, comp, force, ntot, n0 if args.scaling == "strong" else rank * nloc, gather)
+        barrier()
 
     # A second, longer region (>= 2 s of steps, no per-kernel events): `value` stays the K steps the
     # contract asks for; this shows that the rate holds when the region is not a quarter of a second.

@@ -212,9 +212,12 @@ def test_gadget_native(tmp_path):
     (d / "snap.info").write_text("not a snapshot")              # no trailing digit: ignored by scanDirectory
     rd = R.ParticleReader.createReader("GadgetNative", [str(d)])
     assert sorted(os.path.basename(f) for f in rd._files) == ["snap.0", "snap.1"]
+    # scanDirectory keeps the directory's own order (the reference iterates std::filesystem::directory_iterator): unspecified, so
+    # the file being read is whichever came first -- its Halo count, not the snapshot's 50
+    first = os.path.basename(rd._files[0])
+    assert rd.CurrentNumber() == {"snap.0": 40, "snap.1": 10}[first]
     rd._files.sort()
     assert rd.GetTypes() == ["Disk", "Gas", "Halo", "Stars"] and rd.CurrentTime() == 0.7
-    assert rd.CurrentNumber() == 40                              # the file being read, not the snapshot
     a = rd.arrays()
     assert len(a["mass"]) == 50 and np.all(a["mass"] == 0.25)
     assert np.array_equal(a["pos"], np.concatenate([f0[0][5:45], f1[0][3:13]]).astype(np.float64))
